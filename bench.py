@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the 1090ES IQ -> Mode S record path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N = 1 (BASELINE configs[1]+[2]): one "step" = one pass of the hot path over one batch: the GPU demodulates 1 GiB of
 synthetic u8 IQ (4096 reference buffers of 262144 B, already resident in HBM) and brings the sorted candidate records
@@ -24,7 +24,8 @@ with the sequential resolver inside gives end_to_end_msamples_per_s.
 Started bare with --gpus N > 1 (no RANK in the environment) the script starts its N ranks itself as child processes
 (python -m torch.distributed.run, rendezvous on 127.0.0.1) before anything touches the GPU and exits with their code.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed step.  --dump-outputs DIR (N = 1, 1090) writes the packed records
+of the last timed step as DIR/records_<field>.npy (float64), for comparing two builds on the same seeded input.
 """
 import argparse
 import json
@@ -77,7 +78,16 @@ def parse_args(argv=None):
                     "multi-rank code path (sharding, record gather, resolve) on a one-GPU box; the numbers mean nothing")
     ap.add_argument("--dump-stream", default=None, help="N > 1: rank 0 writes the gathered records and the resolved callback stream (frames, "
                     "aircraft snapshots) of the last step to this .npz file, for the parity test (small --mib only)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="N = 1, --workload 1090: after the run, write the packed records of the last "
+                    "timed step to DIR, one float64 .npy per field (records_<field>.npy) and records_index.npy, which records they are: all of them, "
+                    "or a fixed seeded sample where all would pass 64 MB.  The inputs are the same on every run with the same arguments, so two "
+                    "builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus != 1 or args.workload != "1090" or args.sharded_step_on_one_rank):
+        ap.error("--dump-outputs: the headline path only (--gpus 1 --workload 1090); --dump-stream covers N > 1")
+    return args
 
 
 def self_launch(args):
@@ -521,7 +531,29 @@ def bench_1090_single(args, local_rank, A, synth, torch):
     sc.close()
     del d_iq
     torch.cuda.empty_cache()
+    if args.dump_outputs:
+        out["dump_outputs"] = dump_records(args.dump_outputs, rec)
     return out
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files of one dump together
+
+
+def dump_records(path, rec):
+    """--dump-outputs: the packed records of the last timed step (what a caller of the headline path receives), one float64 array per field
+    in path/records_<field>.npy (every field is an integer of at most 32 bits: exact in float64), and path/records_index.npy, the indices of
+    the records written: all of them, or a fixed seeded sample, in order, where all of them would pass DUMP_LIMIT_BYTES."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = rec.dtype.names
+    nfiles = len(names) + 1
+    keep = (DUMP_LIMIT_BYTES - 128 * nfiles) // (8 * nfiles)  # (128: the .npy header)
+    n = len(rec)
+    idx = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0x1090AD5B).choice(n, keep, replace=False))
+    np.save(os.path.join(path, "records_index.npy"), idx.astype(np.float64))
+    for f in names:
+        np.save(os.path.join(path, "records_%s.npy" % f), rec[f][idx].astype(np.float64))
+    return {"dir": path, "records": n, "written": int(len(idx)), "fields": list(names)}
 
 
 def recovered_2400(A, synth, local_rank, nbuf=16):

@@ -64,7 +64,7 @@ struct IDataProvider
 };
 
 // State record the traffic manager owns: the reference's members in the reference's order (AircraftImpl.h:26-44), so that the object has the same
-// size and every member the same offset under either header (held equal at compile time by tests/cpp/iface_matches_reference.cpp).  The six cpr*
+// size and every member the same offset under either header (held equal by tests/test_iface_matches_reference.py).  The six cpr*
 // members are the reference demodulator's scratch for its even/odd pair; the GPU handler keeps that state in its resolver and leaves them untouched.
 struct AirCraftImpl : IAirCraft
 {

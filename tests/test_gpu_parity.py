@@ -498,6 +498,29 @@ def test_bench_sharded_file_step_two_ranks_rehearsal(native_libs, tmp_path):
     assert line["record_transport_by_rank"] == ["NodeGather", "NodeGather"] and line["record_transports_agree"] is True
 
 
+def test_bench_dump_outputs_are_the_last_timed_steps_records(native_libs, tmp_path):
+    """`bench.py --dump-outputs DIR` (the headline path, one GPU): the packed records of the last timed step, one float64 .npy per field, must be
+    the oracle's records of the same seeded input with the host build's decoded fields, every one of them (small enough for no sampling)."""
+    import json
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = _run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--mib", "16", "--steps", "3", "--warmup", "1", "--cpu-buffers", "0",
+                "--no-extras", "--dump-outputs", str(tmp_path)])
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-6000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    whole, _ = synth.fill_range(0, 64)
+    want = O.expected_records(whole, BB, dtype=A.RECORD_DTYPE)
+    want = A.pack_records(want, A.decode_records_host(want))
+    assert line["dump_outputs"]["records"] == line["dump_outputs"]["written"] == len(want) == line["records_per_step"]
+    idx = np.load(tmp_path / "records_index.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.arange(len(want)))
+    for f in A.PACKED_DTYPE.names:
+        got = np.load(tmp_path / ("records_%s.npy" % f))
+        assert got.dtype == np.float64 and np.array_equal(got, want[f].astype(np.float64)), f
+
+
 def _gpu_count():
     import torch
     return torch.cuda.device_count()  # (does not initialise the GPU in this process)
