@@ -37,7 +37,7 @@ extern "C" {
 #define ADSB_AMD_EINVAL (-2)   /* bad argument (size, alignment, slot) */
 #define ADSB_AMD_EHIP (-3)     /* HIP runtime error during a call */
 #define ADSB_AMD_ENOSPC (-4)   /* caller's output array too small (n_out holds the needed count) */
-#define ADSB_AMD_ESTATE (-5)   /* fetch without submit, etc. */
+#define ADSB_AMD_ESTATE (-5)   /* fetch without submit, a fetch between fetch_packed_begin and _end, etc. */
 #define ADSB_AMD_ENOMEM (-6)   /* the record regions an input would need do not fit in free device memory */
 
 /* RTLSDR::BufferLength (RTLSDR.hpp:55): the unit the reference demodulates independently. */
@@ -170,6 +170,14 @@ int adsb_amd_scan_1090(adsb_amd_ctx_t* ctx, const uint8_t* iq_host, size_t nbyte
  * work), or by a launch of its own when the scan is fetched first.  A loop may therefore alternate its submits over two streams with three slots
  * in flight: a scan kernel then starts while the one before it drains, and the step costs what the kernel alone costs (profiles/r06_two_streams.txt);
  * the fetch order, and the rule that a slot's next submit follows its fetch (or fetch_packed_begin), stay as they are.
+ * A slot's life, and what the library guarantees along it:
+ *   - A fetch of any form ends the slot's scan, and so does a fetch the library refuses because the scan did not produce the array asked for
+ *     (adsb_amd_set_outputs): a refused fetch consumes the scan, whose records are then lost; the slot is ready for its next submit either way.
+ *   - Between adsb_amd_scan_1090_fetch_packed_begin and _end the slot may be resubmitted but not fetched: every fetch of it, of any form, returns
+ *     ADSB_AMD_ESTATE and leaves the scan submitted beside the copy to be fetched after _end.
+ *   - A device fetch on a caller's stream may return before its copy has run; the library orders that copy before the slot's next ordering pass
+ *     (the caller need not wait for it before resubmitting the slot).
+ *   - A slot may be resubmitted on a different stream from the one that ran its last scan and ordering pass.
  */
 #define ADSB_AMD_SLOTS 3
 int adsb_amd_scan_1090_submit(adsb_amd_ctx_t* ctx, const void* iq_device, size_t nbytes, size_t buffer_bytes,
@@ -180,7 +188,7 @@ int adsb_amd_scan_1090_fetch(adsb_amd_ctx_t* ctx, int slot, const adsb_amd_recor
 int adsb_amd_scan_1090_fetch_decoded(adsb_amd_ctx_t* ctx, int slot, const adsb_amd_record_t** records, const adsb_amd_decoded_t** decoded,
                                      size_t* n);
 /* Which arrays the ordering pass produces, from the next submit on (default ADSB_AMD_OUT_RECORDS | ADSB_AMD_OUT_DECODED).  A fetch of
- * an array the slot's scan did not produce returns ADSB_AMD_ESTATE. */
+ * an array the slot's scan did not produce returns ADSB_AMD_ESTATE and consumes the scan. */
 #define ADSB_AMD_OUT_RECORDS 1u
 #define ADSB_AMD_OUT_DECODED 2u
 #define ADSB_AMD_OUT_PACKED 4u
@@ -189,7 +197,7 @@ int adsb_amd_set_outputs(adsb_amd_ctx_t* ctx, unsigned mask);
 int adsb_amd_scan_1090_fetch_packed(adsb_amd_ctx_t* ctx, int slot, const adsb_amd_packed_t** packed, size_t* n);
 /* The same fetch in two halves, for a loop that keeps the GPU fed: _begin waits for the slot's count (*n), starts the copy of the packed records and
  * leaves the slot free for its next adsb_amd_scan_1090_submit; _end waits for that copy and returns the pointer (valid until the slot's next _begin or
- * fetch).  Every _begin has to be followed by its _end before the slot is fetched again. */
+ * fetch).  Every _begin has to be followed by its _end before the slot is fetched again (until then a fetch returns ADSB_AMD_ESTATE). */
 int adsb_amd_scan_1090_fetch_packed_begin(adsb_amd_ctx_t* ctx, int slot, size_t* n);
 int adsb_amd_scan_1090_fetch_packed_end(adsb_amd_ctx_t* ctx, int slot, const adsb_amd_packed_t** packed, size_t* n);
 /* The same wait, but the sorted records are copied into `dst_device` (room for `cap` records: memory of the same GPU, or page-locked /
@@ -207,6 +215,10 @@ int adsb_amd_scan_1090_timing(adsb_amd_ctx_t* ctx, int slot, float* scan_kernel_
  * all; 0: none).  An event costs the scan's stream 3-5 us, two of them 3 % of a 1 GiB scan: a caller that pipelines scans back to back
  * and wants the kernel time as a running figure samples it. */
 int adsb_amd_set_timing(adsb_amd_ctx_t* ctx, unsigned every);
+/* Test hook: synchronises the device and counts, in *nonzero, the words of the slot's state that its next scan needs zero -- its work counters and
+ * the block-sum array that scan will add into.  0 after every way a scan can leave the slot.  ADSB_AMD_ESTATE while the slot has a scan in flight
+ * or a fetch begun and not ended. */
+int adsb_amd_debug_slot_dirty(adsb_amd_ctx_t* ctx, int slot, size_t* nonzero);
 
 /* Parity helper: magnitudes exactly as ADSB1090.cpp:165-173 computes them (n = nbytes/2 values). */
 int adsb_amd_magnitude_1090(adsb_amd_ctx_t* ctx, const uint8_t* iq_host, size_t nbytes, uint16_t* mag_out);

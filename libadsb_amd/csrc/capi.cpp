@@ -61,11 +61,16 @@ struct Slot
     hipEvent_t         ev_scan0 = nullptr, ev_scan1 = nullptr, ev_order = nullptr;
     uint32_t           seq = 0;            // launches of this slot: the stamp the ordering pass writes beside the count
     bool               pending = false, timed = false;
+    bool               counted = false;    // the host has seen this scan's count: its ordering pass has done all of its work (retire)
     // Round 6: the slot's ordering pass is not launched with its scan.  The NEXT scan kernel on the same stream (the other slot's) does it in front of
     // its own work (gather1090.hip.h) -- `gather_attached` --, or, when the slot is waited for before any such kernel came, a launch of its own does.
     bool               gather_launched = false, gather_attached = false;
     bool               copying = false;  // adsb_amd_scan_1090_fetch_packed_begin has put the slot's records on the copy stream; _end has not been called
     size_t             copy_n  = 0;      // their number
+    // adsb_amd_scan_1090_fetch_device on a caller's stream returns with the copy of the dense arrays still queued there; the slot's next ordering
+    // pass rewrites them, and the stream that launches it first waits for this event while it has not completed (wait_copy)
+    hipEvent_t         ev_copy   = nullptr;
+    bool               copy_live = false;
     uint32_t*          next_sums = nullptr; // the sum array this scan's ordering pass zeroes (the slot's other one)
     unsigned long long submit_no = 0;       // adsb_amd_ctx::submit_no when this scan was enqueued
     bool               events = false;     // this scan has the two timing events around its kernel
@@ -144,7 +149,8 @@ void free_slot(Slot& s)
     s.chunks_cap = s.cap_per_chunk = 0;
 }
 
-int ensure_slot(adsb_amd_ctx* c, Slot& s, size_t chunks, size_t cap, unsigned mask)
+// (the arrays are zeroed on `stream`, the one the slot's scan is about to be launched on: the context's streams do not wait for the null stream)
+int ensure_slot(adsb_amd_ctx* c, Slot& s, size_t chunks, size_t cap, unsigned mask, hipStream_t stream)
 {
     if (chunks <= s.chunks_cap && cap == s.cap_per_chunk)
     {
@@ -157,7 +163,7 @@ int ensure_slot(adsb_amd_ctx* c, Slot& s, size_t chunks, size_t cap, unsigned ma
     s.sums_words = sums_entries(nch) * kSumStride;
     s.sums_phase = 0;
     HIP_TRY(c, hipMalloc(&s.block_sums, 2 * s.sums_words * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemset(s.block_sums, 0, 2 * s.sums_words * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemsetAsync(s.block_sums, 0, 2 * s.sums_words * sizeof(uint32_t), stream));
     HIP_TRY(c, hipMalloc(&s.regions, nch * cap * sizeof(adsb_amd_record_t)));
     HIP_TRY(c, hipMalloc(&s.dense, nch * cap * sizeof(adsb_amd_record_t)));
     HIP_TRY(c, hipMalloc(&s.decoded, nch * cap * sizeof(adsb_amd_decoded_t)));
@@ -241,6 +247,22 @@ GatherArgs gather_args(const Slot& s)
     return g;
 }
 
+// Make `stream` wait for the slot's last device fetch on a caller's stream, if that copy has not run yet: called before a launch that runs the slot's
+// next ordering pass.  (A copy that is done costs nothing, not even a packet: the loops of bench.py have waited for theirs by then.)
+int wait_copy(adsb_amd_ctx* c, Slot& s, hipStream_t stream)
+{
+    if (!s.copy_live) return ADSB_AMD_OK;
+    const hipError_t q = hipEventQuery(s.ev_copy);
+    if (q == hipErrorNotReady) HIP_TRY(c, hipStreamWaitEvent(stream, s.ev_copy, 0));
+    else if (q != hipSuccess)
+    {
+        c->error = std::string("device fetch failed: ") + hipGetErrorString(q);
+        return ADSB_AMD_EHIP;
+    }
+    s.copy_live = false;
+    return ADSB_AMD_OK;
+}
+
 int enqueue(adsb_amd_ctx* c, Slot& s)
 {
     s.args.chunk_records = s.regions;
@@ -266,12 +288,19 @@ int enqueue(adsb_amd_ctx* c, Slot& s)
     // their own work (round 6).
     Slot* op = nullptr;
     for (Slot& x : c->slot)
-        if (&x != &s && x.pending && !x.gather_launched && x.stream == s.stream && x.args.total_chunks != 0 && (!op || x.submit_no < op->submit_no)) op = &x;
+        if (&x != &s && x.pending && !x.copying && !x.gather_launched && x.stream == s.stream && x.args.total_chunks != 0 && (!op || x.submit_no < op->submit_no)) op = &x;
+    // (not the pass of a slot whose packed records a begun fetch is still copying: that pass rewrites them; it runs once the fetch has ended)
     const bool        attach = op != nullptr && s.args.total_chunks != 0;
     Slot&             o      = attach ? *op : s;
     const GatherArgs  ga     = attach ? gather_args(o) : GatherArgs{};
     const GatherArgs* gp     = attach ? &ga : nullptr;
+    if (attach)
+    {
+        const int rc = wait_copy(c, o, s.stream);
+        if (rc) return rc;
+    }
     s.submit_no              = ++c->submit_no;
+    s.counted                = false;
     if (c->mode == ADSB_AMD_MODE_2400) HIP_TRY(c, launch_scan2400(s.args, s.total_d, s.stream, s.events ? s.ev_scan0 : nullptr, s.events ? s.ev_scan1 : nullptr, gp));
     else HIP_TRY(c, launch_scan1090(s.args, s.total_d, s.stream, s.events ? s.ev_scan0 : nullptr, s.events ? s.ev_scan1 : nullptr, gp));
     if (attach) o.gather_launched = o.gather_attached = true;
@@ -289,8 +318,38 @@ int enqueue(adsb_amd_ctx* c, Slot& s)
 int ensure_gather(adsb_amd_ctx* c, Slot& s)
 {
     if (s.gather_launched) return ADSB_AMD_OK;
+    {
+        const int rc = wait_copy(c, s, s.stream);
+        if (rc) return rc;
+    }
     HIP_TRY(c, launch_gather1090(gather_args(s), s.stream, s.ev_order));
     s.gather_launched = true, s.gather_attached = false;
+    return ADSB_AMD_OK;
+}
+
+// Ends the slot's scan: every path that clears `pending` -- a fetch that succeeded, was refused or failed, a replay that gave up -- comes here.
+// The ordering pass does more than order the records: it zeroes the slot's work counters and the sum array its NEXT scan adds into
+// (gather1090.hip.h), so a scan whose count the host has not seen still gets its pass, and the call returns once the pass has run (the slot's
+// next scan may go to another stream).  A scan whose count has been seen costs nothing here: its pass has finished.
+int retire(adsb_amd_ctx* c, Slot& s)
+{
+    if (!s.pending) return ADSB_AMD_OK;
+    s.pending = false;
+    if (s.counted) return ADSB_AMD_OK;
+    const int rc = ensure_gather(c, s);
+    if (rc) return rc;
+    // (an attached pass rides in a later kernel on the slot's own stream)
+    HIP_TRY(c, s.gather_attached ? hipStreamSynchronize(s.stream) : hipEventSynchronize(s.ev_order));
+    return ADSB_AMD_OK;
+}
+
+// What every fetch checks first.  A refusal here leaves the slot's scan in flight: a scan submitted beside a begun fetch is fetched after its _end.
+int fetchable(adsb_amd_ctx* c, int slot)
+{
+    if (slot < 0 || slot >= kSlots) return fail(c, ADSB_AMD_EINVAL, "slot must be 0, 1 or 2");
+    const Slot& s = c->slot[slot];
+    if (!s.pending) return fail(c, ADSB_AMD_ESTATE, "fetch without submit");
+    if (s.copying) return fail(c, ADSB_AMD_ESTATE, "the slot's last fetch has been begun and not ended");
     return ADSB_AMD_OK;
 }
 } // namespace
@@ -388,6 +447,7 @@ extern "C" int adsb_amd_create_mode(adsb_amd_ctx_t** out, int device, int mode)
         if ((e = hipEventCreateWithFlags(&s.ev_scan0, hipEventDisableSystemFence)) != hipSuccess) return bail("hipEventCreate", e);
         if ((e = hipEventCreateWithFlags(&s.ev_scan1, hipEventDisableSystemFence)) != hipSuccess) return bail("hipEventCreate", e);
         if ((e = hipEventCreateWithFlags(&s.ev_order, hipEventDisableSystemFence)) != hipSuccess) return bail("hipEventCreate", e);
+        if ((e = hipEventCreateWithFlags(&s.ev_copy, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     }
     if constexpr (diag::kStamps)
     {
@@ -450,6 +510,7 @@ extern "C" void adsb_amd_destroy(adsb_amd_ctx_t* c)
         if (s.ev_scan0) (void)hipEventDestroy(s.ev_scan0);
         if (s.ev_scan1) (void)hipEventDestroy(s.ev_scan1);
         if (s.ev_order) (void)hipEventDestroy(s.ev_order);
+        if (s.ev_copy) (void)hipEventDestroy(s.ev_copy);
     }
     if (c->crc_tab) (void)hipFree(c->crc_tab);
     if (c->lut978) (void)hipFree(c->lut978);
@@ -475,10 +536,11 @@ extern "C" int adsb_amd_scan_1090_submit(adsb_amd_ctx_t* c, const void* iq_devic
     if (rc) return rc;
     size_t cap = s.cap_per_chunk ? s.cap_per_chunk : kDefaultCap;
     if (s.cap_hint > cap) cap = s.cap_hint; // another slot had to grow its regions for this kind of input
-    if ((rc = ensure_slot(c, s, a.total_chunks, cap, c->outputs))) return rc;
+    const hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if ((rc = ensure_slot(c, s, a.total_chunks, cap, c->outputs, stream))) return rc;
     s.produced = c->outputs;
     s.args     = a;
-    s.stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    s.stream   = stream;
     if ((rc = enqueue(c, s))) return rc;
     s.pending = true;
     return ADSB_AMD_OK;
@@ -507,6 +569,7 @@ int wait_count(adsb_amd_ctx* c, Slot& s)
         {
             s.nrecords = (uint32_t)w;
             s.overflow = ((w >> 32) & 1u) != 0;
+            s.counted  = true;
             return ADSB_AMD_OK;
         }
         if ((spins & 0x3FFu) == 0x3FFu)
@@ -522,6 +585,7 @@ int wait_count(adsb_amd_ctx* c, Slot& s)
                     {
                         s.nrecords = (uint32_t)w2;
                         s.overflow = ((w2 >> 32) & 1u) != 0;
+                        s.counted  = true;
                         return ADSB_AMD_OK;
                     }
                     __builtin_ia32_pause();
@@ -563,7 +627,7 @@ int wait_scan(adsb_amd_ctx* c, Slot& s)
                        std::to_string((free_b + have) >> 20) + " MiB free: split the input into smaller scan calls";
             return ADSB_AMD_ENOMEM;
         }
-        int rc = ensure_slot(c, s, s.args.total_chunks, cap, s.produced);
+        int rc = ensure_slot(c, s, s.args.total_chunks, cap, s.produced, s.stream);
         if (rc == ADSB_AMD_OK) rc = enqueue(c, s);
         if (rc) return rc;
         for (Slot& other : c->slot)
@@ -581,7 +645,7 @@ void read_timing(Slot& s)
     else s.timed = s.timed && hipEventElapsedTime(&s.total_ms, s.ev_scan0, s.ev_order) == hipSuccess;
 }
 
-// Body of fetch; the caller clears `pending` whatever the outcome, so a failed sync or copy never wedges the slot.  `what`: ADSB_AMD_OUT_* to
+// Body of fetch; the caller retires the scan whatever the outcome, so a refusal, a failed sync or copy never wedges the slot nor skips its pass.  `what`: ADSB_AMD_OUT_* to
 // bring to the host.
 int fetch_slot(adsb_amd_ctx* c, Slot& s, unsigned what)
 {
@@ -634,12 +698,11 @@ extern "C" int adsb_amd_set_timing(adsb_amd_ctx_t* c, unsigned every)
 extern "C" int adsb_amd_scan_1090_fetch_packed(adsb_amd_ctx_t* c, int slot, const adsb_amd_packed_t** packed, size_t* n)
 {
     if (!c) return ADSB_AMD_EINVAL;
-    if (slot < 0 || slot >= kSlots) return fail(c, ADSB_AMD_EINVAL, "slot must be 0, 1 or 2");
-    Slot& s = c->slot[slot];
-    if (!s.pending) return fail(c, ADSB_AMD_ESTATE, "fetch without submit");
-    const int rc = fetch_slot(c, s, ADSB_AMD_OUT_PACKED);
-    s.pending    = false;
+    if (const int rc = fetchable(c, slot)) return rc;
+    Slot&     s  = c->slot[slot];
+    const int rc = fetch_slot(c, s, ADSB_AMD_OUT_PACKED), rr = retire(c, s);
     if (rc) return rc;
+    if (rr) return rr;
     if (packed) *packed = s.host_packed;
     if (n) *n = s.nrecords;
     return ADSB_AMD_OK;
@@ -654,10 +717,8 @@ extern "C" int adsb_amd_scan_1090_fetch_packed(adsb_amd_ctx_t* c, int slot, cons
 extern "C" int adsb_amd_scan_1090_fetch_packed_begin(adsb_amd_ctx_t* c, int slot, size_t* n)
 {
     if (!c) return ADSB_AMD_EINVAL;
-    if (slot < 0 || slot >= kSlots) return fail(c, ADSB_AMD_EINVAL, "slot must be 0, 1 or 2");
+    if (const int rc = fetchable(c, slot)) return rc;
     Slot& s = c->slot[slot];
-    if (!s.pending) return fail(c, ADSB_AMD_ESTATE, "fetch without submit");
-    if (s.copying) return fail(c, ADSB_AMD_ESTATE, "the slot's last fetch has been begun and not ended");
     auto body = [&]() -> int {
         HIP_TRY(c, hipSetDevice(c->device));
         if (!(s.produced & ADSB_AMD_OUT_PACKED)) return fail(c, ADSB_AMD_ESTATE, "this slot's scan did not produce the packed form (adsb_amd_set_outputs before the submit)");
@@ -670,10 +731,10 @@ extern "C" int adsb_amd_scan_1090_fetch_packed_begin(adsb_amd_ctx_t* c, int slot
         s.copy_n = s.nrecords, s.copying = true;
         return ADSB_AMD_OK;
     };
-    const int rc = body();
-    s.pending    = false;
-    if (rc == ADSB_AMD_OK && n) *n = s.copy_n;
-    return rc;
+    const int rc = body(), rr = retire(c, s);
+    if (rc) return rc;
+    if (n) *n = s.copy_n;
+    return rr;
 }
 extern "C" int adsb_amd_scan_1090_fetch_packed_end(adsb_amd_ctx_t* c, int slot, const adsb_amd_packed_t** packed, size_t* n)
 {
@@ -694,12 +755,11 @@ extern "C" int adsb_amd_scan_1090_fetch_packed_end(adsb_amd_ctx_t* c, int slot, 
 extern "C" int adsb_amd_scan_1090_fetch(adsb_amd_ctx_t* c, int slot, const adsb_amd_record_t** records, size_t* n)
 {
     if (!c) return ADSB_AMD_EINVAL;
-    if (slot < 0 || slot >= kSlots) return fail(c, ADSB_AMD_EINVAL, "slot must be 0, 1 or 2");
-    Slot& s = c->slot[slot];
-    if (!s.pending) return fail(c, ADSB_AMD_ESTATE, "fetch without submit");
-    const int rc = fetch_slot(c, s, ADSB_AMD_OUT_RECORDS);
-    s.pending    = false;
+    if (const int rc = fetchable(c, slot)) return rc;
+    Slot&     s  = c->slot[slot];
+    const int rc = fetch_slot(c, s, ADSB_AMD_OUT_RECORDS), rr = retire(c, s);
     if (rc) return rc;
+    if (rr) return rr;
     if (records) *records = s.host;
     if (n) *n = s.nrecords;
     return ADSB_AMD_OK;
@@ -709,12 +769,11 @@ extern "C" int adsb_amd_scan_1090_fetch_decoded(adsb_amd_ctx_t* c, int slot, con
                                                 size_t* n)
 {
     if (!c) return ADSB_AMD_EINVAL;
-    if (slot < 0 || slot >= kSlots) return fail(c, ADSB_AMD_EINVAL, "slot must be 0, 1 or 2");
-    Slot& s = c->slot[slot];
-    if (!s.pending) return fail(c, ADSB_AMD_ESTATE, "fetch without submit");
-    const int rc = fetch_slot(c, s, ADSB_AMD_OUT_RECORDS | ADSB_AMD_OUT_DECODED);
-    s.pending    = false;
+    if (const int rc = fetchable(c, slot)) return rc;
+    Slot&     s  = c->slot[slot];
+    const int rc = fetch_slot(c, s, ADSB_AMD_OUT_RECORDS | ADSB_AMD_OUT_DECODED), rr = retire(c, s);
     if (rc) return rc;
+    if (rr) return rr;
     if (records) *records = s.host;
     if (decoded) *decoded = s.host_dec;
     if (n) *n = s.nrecords;
@@ -742,9 +801,8 @@ namespace
 int fetch_device_impl(adsb_amd_ctx_t* c, int slot, void* dst_device, size_t cap, void* hip_stream, size_t* n, bool packed)
 {
     if (!c) return ADSB_AMD_EINVAL;
-    if (slot < 0 || slot >= kSlots) return fail(c, ADSB_AMD_EINVAL, "slot must be 0, 1 or 2");
+    if (const int rc = fetchable(c, slot)) return rc;
     Slot& s = c->slot[slot];
-    if (!s.pending) return fail(c, ADSB_AMD_ESTATE, "fetch without submit");
     auto body = [&]() -> int {
         HIP_TRY(c, hipSetDevice(c->device));
         {
@@ -764,15 +822,36 @@ int fetch_device_impl(adsb_amd_ctx_t* c, int slot, void* dst_device, size_t cap,
             HIP_TRY(c, hipMemcpyAsync(dst_device, packed ? static_cast<const void*>(s.packed) : static_cast<const void*>(s.dense),
                                       s.nrecords * sizeof(adsb_amd_record_t), hipMemcpyDefault, st));
             if (!hip_stream) HIP_TRY(c, hipStreamSynchronize(st));
+            else
+            { // the copy outlives the call: the slot's next ordering pass waits for it (wait_copy)
+                HIP_TRY(c, hipEventRecord(s.ev_copy, st));
+                s.copy_live = true;
+            }
         }
         read_timing(s);
         return ADSB_AMD_OK;
     };
-    const int rc = body();
-    s.pending    = false;
-    return rc;
+    const int rc = body(), rr = retire(c, s);
+    return rc ? rc : rr;
 }
 } // namespace
+
+extern "C" int adsb_amd_debug_slot_dirty(adsb_amd_ctx_t* c, int slot, size_t* nonzero)
+{
+    if (!c || !nonzero) return ADSB_AMD_EINVAL;
+    if (slot < 0 || slot >= kSlots) return fail(c, ADSB_AMD_EINVAL, "slot must be 0, 1 or 2");
+    Slot& s = c->slot[slot];
+    if (s.pending || s.copying) return fail(c, ADSB_AMD_ESTATE, "the slot has a scan in flight or a fetch begun and not ended");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipDeviceSynchronize());
+    std::vector<uint32_t> w((size_t)kWorkCounters * kCounterStride + (s.block_sums ? s.sums_words : 0));
+    HIP_TRY(c, hipMemcpy(w.data(), s.work_d, (size_t)kWorkCounters * kCounterStride * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (s.block_sums)
+        HIP_TRY(c, hipMemcpy(w.data() + (size_t)kWorkCounters * kCounterStride, s.block_sums + (size_t)s.sums_phase * s.sums_words, s.sums_words * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost));
+    *nonzero = (size_t)std::count_if(w.begin(), w.end(), [](uint32_t x) { return x != 0; });
+    return ADSB_AMD_OK;
+}
 
 extern "C" int adsb_amd_scan_1090_timing(adsb_amd_ctx_t* c, int slot, float* scan_kernel_ms, float* total_ms)
 {
@@ -1109,8 +1188,8 @@ extern "C" long adsb_amd_handler_replay_file(adsb_amd_handler_t* h, const char* 
     }
     uploader.join();
     for (auto& t : readers) t.join();
+    for (Slot& sl : c->slot) (void)retire(c, sl); // a failed run may leave a submitted scan behind: it still gets its ordering pass
     (void)hipDeviceSynchronize();
-    for (Slot& sl : c->slot) sl.pending = false; // a failed run may leave a submitted scan behind
     if (failed && !rc)
     {
         h->error = "replay_file: upload failed";

@@ -249,14 +249,17 @@ __device__ __forceinline__ uint32_t gather_unit(const GatherArgs& ga, uint32_t B
 // finishes the last shard is the pass's LAST FINISHER and tells the host.
 __device__ __forceinline__ void gather_unit_and_ticket(const GatherArgs& ga, uint32_t u, uint32_t units, uint32_t split, GatherLds& lds, uint32_t lane)
 {
-    // housekeeping, spread over the units: the slot's other sum array (all of it: the next input may be larger) and its work counters start from zero
-    for (uint32_t k = u * 64u + lane; k < 2u * ga.next_entries; k += units * 64u) ga.next_block_sums[(k >> 1) * kSumStride + (k & 1u)] = 0;
+    // housekeeping, spread over the units: the slot's other sum array (all of it: the next input may be larger) and its work counters start from zero.
+    // Written through to memory (agent-scope stores: `sc1`), not left in this XCD's L2: the host may resubmit the slot on another stream as soon as it
+    // sees the count, and that scan's atomics on other XCDs, which the per-XCD L2s do not keep coherent, must find the zeroes.
+    for (uint32_t k = u * 64u + lane; k < 2u * ga.next_entries; k += units * 64u)
+        __hip_atomic_store(&ga.next_block_sums[(k >> 1) * kSumStride + (k & 1u)], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (u == 0)
-        for (uint32_t k = lane; k < kWorkCounters; k += 64u) ga.work_counters[k * kCounterStride] = 0;
+        for (uint32_t k = lane; k < kWorkCounters; k += 64u) __hip_atomic_store(&ga.work_counters[k * kCounterStride], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t B = u / split, q = u % split;
     const uint32_t moved = gather_unit(ga, B, q, split, lds, lane);
     const bool     over  = q == 0 && ga.block_sums[B * kSumStride + 1] != 0; // some chunk of this block overflowed its region
-    // Everything this wave stored has been acknowledged -- the records by memory, the zeroes by the L2 -- before its ticket counts.
+    // Everything this wave stored has been acknowledged by memory -- the records and the zeroes -- before its ticket counts.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     uint32_t last_total = 0xFFFFFFFFu; // lane 0 of the pass's last finisher: the pass's record count
     bool     any_over   = false;

@@ -350,6 +350,21 @@ def test_split_fetch_refuses_calls_out_of_order(native_libs):
     sc.set_outputs(A.OUT_PACKED)
     sc.submit(d.data_ptr(), d.numel(), BB, st, 0)
     assert sc.fetch_packed(0, copy=True).tobytes() == first.tobytes()
+    # begin(A), submit(A), then a submit of ANOTHER slot on the same stream: that kernel must not take on the ordering pass of A's new scan (it would
+    # rewrite A's packed records under the copy).  _end returns A's first input, the fetches after it A's second input and the other slot's.
+    iq2, _ = synth.fill_range(95, 8, cfg=synth.default_cfg(mean_spacing=300))
+    d2 = torch.from_numpy(iq2).cuda()
+    sc.submit(d2.data_ptr(), d2.numel(), BB, st, 2)
+    second = sc.fetch_packed(2, copy=True)
+    assert len(second) != len(first)
+    sc.submit(d.data_ptr(), d.numel(), BB, st, 1)
+    n = sc.fetch_packed_begin(1)
+    sc.submit(d2.data_ptr(), d2.numel(), BB, st, 1)
+    sc.submit(d.data_ptr(), d.numel(), BB, st, 0)
+    got = sc.fetch_packed_end(1, copy=True)
+    assert len(got) == n and got.tobytes() == first.tobytes()
+    assert sc.fetch_packed(1, copy=True).tobytes() == second.tobytes()
+    assert sc.fetch_packed(0, copy=True).tobytes() == first.tobytes()
     sc.close()
 
 
