@@ -414,6 +414,53 @@ void init_fec(void);
 int  process_buffer(const uint16_t* phi, int len, uint64_t offset);
 void adsb_amd_uat_set_dump_raw_message(adsb_amd_dump_raw_message_fn fn);
 
+/* ---- UAT 978 aircraft tracking: what uat2json-wrapper.cpp:14-122 does with a frame (dump978's uat_decode_adsb_mdb, then the
+ * sticky copy onto the aircraft), with the decoding on the GPU (libadsb_amd/csrc/mdb978.h, one source for host and device).
+ * One packed record per frame: */
+#define ADSB_AMD_UAT_SV       0x01u /* the type carries a state vector (0-10) */
+#define ADSB_AMD_UAT_POSITION 0x02u /* lat1e7 / lon1e7 */
+#define ADSB_AMD_UAT_ALTITUDE 0x04u /* baro or geometric: the wrapper takes either */
+#define ADSB_AMD_UAT_SPEED    0x08u
+#define ADSB_AMD_UAT_TRACK    0x10u
+#define ADSB_AMD_UAT_VERTRATE 0x20u
+#define ADSB_AMD_UAT_CALLSIGN 0x40u /* mode status with callsign_type == CS_CALLSIGN (CSID set, first character not NUL) */
+typedef struct adsb_amd_uat_mdb
+{
+    uint32_t address;   /* header bytes 1-3; the address qualifier is ignored, as the wrapper ignores it */
+    uint8_t  mdb_type;  /* header byte 0 >> 3 */
+    uint8_t  valid;     /* ADSB_AMD_UAT_* */
+    uint16_t track;     /* degrees */
+    int32_t  lat1e7, lon1e7;
+    int32_t  altitude;  /* feet */
+    uint16_t speed;     /* knots */
+    int16_t  vert_rate; /* feet per minute */
+    char     callsign[8]; /* trailing spaces as NUL, as dump978 trims them */
+} adsb_amd_uat_mdb_t;
+
+/* One reported frame: the frame callback's fields and the decoded record.  An adapter over a shared traffic manager applies the
+ * delta (mdb.valid) itself; `aircraft` in the callback is this handle's own view of the address after the update. */
+typedef struct adsb_amd_uat_update
+{
+    uint64_t           sample_index;
+    int32_t            rs_errors;
+    char               updown; /* '-' downlink, '+' uplink: the wrapper decodes both as an ADS-B MDB */
+    uint8_t            reserved[3];
+    adsb_amd_uat_mdb_t mdb;
+} adsb_amd_uat_update_t;
+typedef void (*adsb_amd_uat_on_changed_fn)(void* user, const adsb_amd_uat_update_t* upd, const adsb_amd_aircraft_t* aircraft);
+
+/* cb != NULL switches tracking on for every entry point that reports frames (handle_data, process_phases, process_iq,
+ * submit_iq / collect): one cb per reported frame, after that frame's frame callback, in stream order.  want_frames == 0: aircraft
+ * only -- the frame callbacks are not made and the frame bytes do not cross the host link, only the records and the decoded
+ * records do.  cb == NULL switches tracking off (the aircraft are kept).  Not while calls are in flight. */
+int adsb_amd_uat_set_tracking(adsb_amd_uat_t* u, adsb_amd_uat_on_changed_fn cb, void* user, int want_frames);
+int adsb_amd_uat_aircraft_count(const adsb_amd_uat_t* u, uint64_t* count);
+int adsb_amd_uat_reset_aircraft(adsb_amd_uat_t* u);
+/* The decoder on its own: `count` frames `stride` bytes apart (bytes past `stride` read as 0), one record each.  The device
+ * form runs the kernel build of the same source. */
+int adsb_amd_uat_mdb_decode(const uint8_t* frames, int count, int stride, adsb_amd_uat_mdb_t* out);
+int adsb_amd_uat_mdb_decode_device(adsb_amd_uat_t* u, const uint8_t* frames, int count, int stride, adsb_amd_uat_mdb_t* out);
+
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,12 @@ FRAME_DTYPE = np.dtype([("offset", "<u8"), ("msg", "u1", (14,)), ("nbits", "u1")
                         ("phase_applied", "u1"), ("df", "u1"), ("reserved", "u1"), ("addr", "<u4")])
 AIRCRAFT_DTYPE = np.dtype([("addr", "<u4"), ("callsign", "S8"), ("lat1e7", "<i4"), ("lon1e7", "<i4"), ("altitude", "<i4"),
                            ("speed", "<u4"), ("track", "<u4"), ("vert_rate", "<i4"), ("squawk", "<u4")])
+# UAT 978 tracking (adsb_amd_uat_mdb_t / adsb_amd_uat_update_t)
+UAT_MDB_DTYPE = np.dtype([("address", "<u4"), ("mdb_type", "u1"), ("valid", "u1"), ("track", "<u2"), ("lat1e7", "<i4"), ("lon1e7", "<i4"),
+                          ("altitude", "<i4"), ("speed", "<u2"), ("vert_rate", "<i2"), ("callsign", "S8")])
+UAT_UPDATE_DTYPE = np.dtype([("sample_index", "<u8"), ("rs_errors", "<i4"), ("updown", "S1"), ("reserved", "u1", (3,)), ("mdb", UAT_MDB_DTYPE)])
+UAT_SV, UAT_POSITION, UAT_ALTITUDE, UAT_SPEED, UAT_TRACK, UAT_VERTRATE, UAT_CALLSIGN = 1, 2, 4, 8, 16, 32, 64
+assert UAT_MDB_DTYPE.itemsize == 32 and UAT_UPDATE_DTYPE.itemsize == 48
 DECODED_DTYPE = np.dtype([("kind", "u1"), ("metype", "u1"), ("mesub", "u1"), ("odd", "u1"), ("altitude", "<i4"), ("a", "<u4"), ("b", "<u4")])
 PACKED_DTYPE = np.dtype([("buffer", "<u4"), ("offset", "<u4"), ("addr", "<u4"), ("reserved", "<u2"), ("nbits", "u1"), ("errorbit", "i1"),
                          ("df", "u1"), ("flags", "u1"), ("kind", "u1"), ("odd", "u1"), ("altitude", "<i4"), ("a", "<u4"), ("b", "<u4")])
@@ -45,6 +51,7 @@ EXPORTS = [
     "adsb_amd_uat_create", "adsb_amd_uat_destroy", "adsb_amd_uat_last_error", "adsb_amd_uat_handle_data", "adsb_amd_uat_set_carry_full", "adsb_amd_uat_set_host_loop", "adsb_amd_uat_set_extra_capacity",
     "adsb_amd_uat_stream_state", "adsb_amd_uat_process_phases", "adsb_amd_uat_process_iq", "adsb_amd_uat_submit_iq", "adsb_amd_uat_max_in_flight", "adsb_amd_uat_part_scan", "adsb_amd_uat_part_finish", "adsb_amd_uat_collect", "adsb_amd_uat_possible_steps", "adsb_amd_uat_check_word", "adsb_amd_uat_timing", "adsb_amd_uat_host_timing", "adsb_amd_uat_phase_lut",
     "adsb_amd_uat_rs_decode", "adsb_amd_uat_rs_decode_device", "adsb_amd_uat_set_dump_raw_message", "init_fec", "process_buffer",
+    "adsb_amd_uat_set_tracking", "adsb_amd_uat_aircraft_count", "adsb_amd_uat_reset_aircraft", "adsb_amd_uat_mdb_decode", "adsb_amd_uat_mdb_decode_device",
 ]
 
 
@@ -168,6 +175,11 @@ def lib():
         L.init_fec.restype = None
         L.process_buffer.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
         L.process_buffer.restype = C.c_int
+        L.adsb_amd_uat_set_tracking.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.adsb_amd_uat_aircraft_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.adsb_amd_uat_reset_aircraft.argtypes = [C.c_void_p]
+        L.adsb_amd_uat_mdb_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.adsb_amd_uat_mdb_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -657,3 +669,67 @@ class Uat978:
         lut = np.empty(65536, dtype=np.uint16)
         self._check(self._l.adsb_amd_uat_phase_lut(self._h, lut.ctypes.data))
         return lut
+
+
+UAT_ON_CHANGED = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def uat_mdb_decode(frames, device_handle=None):
+    """The UAT MDB decoder (mdb978.h) on a (count, stride) uint8 array of frames (bytes past `stride` read as 0): the host build,
+    or the kernel build when a Uat978 / Handler978 is given.  Returns UAT_MDB_DTYPE[count]."""
+    f = np.ascontiguousarray(frames, dtype=np.uint8)
+    assert f.ndim == 2
+    out = np.zeros(f.shape[0], dtype=UAT_MDB_DTYPE)
+    L = lib()
+    if device_handle is None:
+        rc = L.adsb_amd_uat_mdb_decode(f.ctypes.data, f.shape[0], f.shape[1], out.ctypes.data)
+    else:
+        rc = L.adsb_amd_uat_mdb_decode_device(device_handle._h, f.ctypes.data, f.shape[0], f.shape[1], out.ctypes.data)
+    if rc != 0:
+        raise AdsbAmdError("UAT MDB decode failed (%d)" % rc)
+    return out
+
+
+class Handler978(Uat978):
+    """UAT 978 with aircraft: one (update, aircraft) row per reported frame, the sticky state of uat2json-wrapper.cpp:18-121
+    (the 978 counterpart of Handler1090).  Frames are decoded on the GPU; set_frames(False) keeps the frame bytes off the host link.
+    The frame-level methods of Uat978 still return the frames (an empty list in aircraft-only mode)."""
+
+    def __init__(self, device=-1, carry_full=False, want_frames=True):
+        super().__init__(device, carry_full)
+        self._updates, self._aircraft = [], []
+        self._on = UAT_ON_CHANGED(self._on_changed)
+        self.set_frames(want_frames)
+
+    def _on_changed(self, _user, upd, aircraft):
+        self._updates.append(C.string_at(upd, 48))
+        self._aircraft.append(C.string_at(aircraft, 40))
+
+    def set_frames(self, want_frames):
+        """False: aircraft only (no frame callbacks; only records and decoded MDBs cross the host link)."""
+        self._check(self._l.adsb_amd_uat_set_tracking(self._h, C.cast(self._on, C.c_void_p), None, 1 if want_frames else 0))
+
+    def take(self):
+        """(updates, aircraft) collected since the last take: UAT_UPDATE_DTYPE and AIRCRAFT_DTYPE arrays, one row per callback."""
+        up = np.frombuffer(b"".join(self._updates), dtype=UAT_UPDATE_DTYPE) if self._updates else np.zeros(0, UAT_UPDATE_DTYPE)
+        ac = np.frombuffer(b"".join(self._aircraft), dtype=AIRCRAFT_DTYPE) if self._aircraft else np.zeros(0, AIRCRAFT_DTYPE)
+        self._updates, self._aircraft = [], []
+        return up, ac
+
+    def handle_data(self, iq):
+        """UAT978Handler::HandleData -> (updates, aircraft)."""
+        super().handle_data(iq)
+        return self.take()
+
+    def process_iq(self, iq, offset=0):
+        """process_buffer over u8 IQ from the host -> (updates, aircraft, consumed)."""
+        _, done = super().process_iq(iq, offset)
+        return self.take() + (done,)
+
+    def aircraft_count(self):
+        n = C.c_uint64()
+        self._check(self._l.adsb_amd_uat_aircraft_count(self._h, C.byref(n)))
+        return n.value
+
+    def reset_aircraft(self):
+        self._check(self._l.adsb_amd_uat_reset_aircraft(self._h))

@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libadsb_amd.so")
 SYNTH = os.path.join(HERE, "libadsb_synth.so")
 
 HIP_SOURCES = ["scan1090.hip", "scan2400.hip", "uat978.hip", "capi.cpp", "resolver1090.cpp", "transport.cpp", "adsb1090_gpu_handler.cpp", "uat978_host.cpp", "uat978_gpu_handler.cpp"]
-HIP_DEPS = HIP_SOURCES + ["scan1090.h", "uat978.h", "rs978.h", "resolver1090.hpp", "decode1090.h", "transport.hpp", "scan_common.hip.h", "gather1090.hip.h", "diag.hip.h", os.path.join(ROOT, "include", "adsb_amd.h"),
+HIP_DEPS = HIP_SOURCES + ["scan1090.h", "uat978.h", "rs978.h", "mdb978.h", "resolver1090.hpp", "decode1090.h", "transport.hpp", "scan_common.hip.h", "gather1090.hip.h", "diag.hip.h", os.path.join(ROOT, "include", "adsb_amd.h"),
                            os.path.join(ROOT, "include", "libadsb_iface.hpp")]
 
 
@@ -73,11 +73,12 @@ def build_synth(force=False):
 
 CXX_TEST = os.path.join(ROOT, "tests", "cpp", "test_1090_gpu")
 CXX_TEST_978 = os.path.join(ROOT, "tests", "cpp", "test_978_gpu")
+CXX_TEST_978_TRACK = os.path.join(ROOT, "tests", "cpp", "test_978_track")
 
 
 def build_cxx_test(force=False):
     """The C++ drop-in test drivers (they use the reference-shaped factories exported by libadsb_amd.so)."""
-    for exe in (CXX_TEST, CXX_TEST_978):
+    for exe in (CXX_TEST, CXX_TEST_978, CXX_TEST_978_TRACK):
         src = exe + ".cpp"
         if not force and not _stale(exe, [src, LIB, os.path.join(ROOT, "include", "libadsb_iface.hpp")]):
             continue

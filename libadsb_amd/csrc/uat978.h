@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "adsb_amd.h"
+
 namespace adsb_amd
 {
 constexpr int kUatSyncBits    = 36;
@@ -120,5 +122,8 @@ hipError_t launch_uat978_demod(const UatArgs& a, uint32_t ncand, bool ordered, h
 // which frames the loop takes.  wide: workgroups of 1024 threads (a call that has the chip to itself) instead of 256 (calls in flight: four waves
 // find room beside another call's demodulation pass, sixteen wait for it)
 hipError_t launch_uat978_decide(const UatArgs& a, uint32_t ncand, const uint32_t* sorted, hipStream_t stream, bool wide);
+// tracking handles: the decoded MDB of each of the first nrec records and of each frame behind a frame the demodulation pass reserved
+hipError_t launch_uat978_mdb(const UatArgs& a, uint32_t nrec, adsb_amd_uat_mdb_t* mdb, adsb_amd_uat_mdb_t* extra_mdb, hipStream_t stream);
+hipError_t launch_uat978_mdb_selftest(const uint8_t* frames, uint32_t count, uint32_t stride, adsb_amd_uat_mdb_t* out, hipStream_t stream);
 hipError_t launch_uat978_rs_selftest(const RsTables* tables, int kind, uint8_t* words, int* results, int count, hipStream_t stream);
 } // namespace adsb_amd

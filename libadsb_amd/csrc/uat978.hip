@@ -25,12 +25,15 @@
 //                          demodulation takes first
 //   uat_succ_kernel +      which frames the dump978 scan loop takes: a successor function over the ordered matches, the path from the
 //   uat_mark_kernel        first one marked by pointer jumping in blocks of 4096 matches
+//   uat_mdb_kernel         tracking handles only: one thread per record and per frame behind a frame, the decoded MDB (mdb978.h) of
+//                          its frame, so that 32 bytes instead of the frame bytes cross the host link
 // The host walks the frames taken (uat978_host.cpp).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 
 #include "diag.hip.h"
+#include "mdb978.h"
 #include "rs978.h"
 #include "uat978.h"
 
@@ -2014,6 +2017,56 @@ hipError_t launch_uat978_rs_selftest(const RsTables* tables, int kind, uint8_t* 
 {
     if (count <= 0) return hipSuccess;
     hipLaunchKernelGGL(uat_rs_selftest_kernel, dim3(count > 4096 ? 4096 : count), dim3(64), 0, stream, tables, kind, words, results, count);
+    return hipGetLastError();
+}
+
+// ---- aircraft tracking (handles that track only): the decoded MDB of every frame the call can report, one thread each.  Threads
+// [0, nrec) take the ordered records (ADS-B frames from the payload array, uplinks from the first bytes of their slot), the rest
+// the frames behind frames (as many as the demodulation pass reserved).  ADS-B and uplink records interleave: nothing here is
+// uniform over a wave.
+__global__ __launch_bounds__(256) void uat_mdb_kernel(const uat_rec_t* __restrict__ recs, const uint8_t* __restrict__ payloads, uint32_t nrec,
+                                                      const uat_extra_t* __restrict__ extras, const uint8_t* __restrict__ extra_payloads,
+                                                      uint32_t extra_cap, const uint32_t* __restrict__ counts, const uint8_t* __restrict__ uplink_payloads,
+                                                      uint32_t uplink_cap, uat_mdb_t* __restrict__ mdb, uat_mdb_t* __restrict__ extra_mdb)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uat_rec_t      r;
+    const uint8_t* pay;
+    uat_mdb_t*     out;
+    if (i < nrec) r = recs[i], pay = payloads + (size_t)i * kUatPayloadStride, out = mdb + i;
+    else
+    {
+        const uint32_t x = i - nrec, nx = min(counts[kUatCountExtras], extra_cap);
+        if (x >= nx) return;
+        r = extras[x].rec, pay = extra_payloads + (size_t)x * kUatPayloadStride, out = extra_mdb + x;
+    }
+    uat_mdb_t m = {};
+    if (r.variant < 2)
+    {
+        if (r.kind == 0) m = decode_mdb_bytes(pay, r.skip == kUatShortSkip ? 18 : 34);
+        else if (r.slot < uplink_cap) m = decode_mdb_bytes(uplink_payloads + (size_t)r.slot * 432, kUatMdbBytes);
+    }
+    *out = m;
+}
+__global__ __launch_bounds__(256) void uat_mdb_selftest_kernel(const uint8_t* __restrict__ frames, uint32_t count, uint32_t stride, uat_mdb_t* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = decode_mdb_bytes(frames + (size_t)i * stride, (int)stride);
+}
+
+hipError_t launch_uat978_mdb(const UatArgs& a, uint32_t nrec, uat_mdb_t* mdb, uat_mdb_t* extra_mdb, hipStream_t stream)
+{
+    const uint32_t n = nrec + a.extra_cap;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(uat_mdb_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a.recs, a.payloads, nrec, a.extras, a.extra_payloads, a.extra_cap,
+                       a.counts, a.uplink_payloads, a.uplink_cap, mdb, extra_mdb);
+    return hipGetLastError();
+}
+
+hipError_t launch_uat978_mdb_selftest(const uint8_t* frames, uint32_t count, uint32_t stride, uat_mdb_t* out, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(uat_mdb_selftest_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, frames, count, stride, out);
     return hipGetLastError();
 }
 

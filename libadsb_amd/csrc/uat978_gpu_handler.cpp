@@ -15,8 +15,12 @@
 //                             (:29); stand-alone adsb_amd::Transport (transport.hpp): the replay of "978000000.test.dat" from the
 //                             working directory through the 16 x 262144-byte ring (RTLSDR.hpp:396-442)
 //   NotifySelfLocation        ignored, as in the reference (:74)
-// dump_raw_message and uat_decode_adsb_mdb stay the host's (uat2json-wrapper.cpp and dump978's uat_decode.c are not
-// part of the demodulation path).  Construction throws when no GPU context can be created: there is no CPU fallback.
+// If the host defines dump_raw_message, frames go there and the host decodes them (uat2json-wrapper.cpp with dump978's
+// uat_decode.c); nothing else happens.  If it does not (the weak symbol is null), the handler tracks aircraft itself, in
+// aircraft-only mode (adsb_amd_uat_set_tracking): the frames are decoded on the GPU (mdb978.h) and each update is applied to the
+// traffic manager as the wrapper applies it (uat2json-wrapper.cpp:18-121: FindOrCreate, the valid fields, sourceId = UAT978,
+// NotifyChanged) -- so a host without dump978 gets aircraft from 978, also on a manager it shares with a 1090 handler.
+// Construction throws when no GPU context can be created: there is no CPU fallback.
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
@@ -47,6 +51,7 @@ struct UAT978GpuHandler final : RTLSDR::IDataHandler, ADSB::IDataProvider
     {
         if (int rc = adsb_amd_uat_create(&gpu, 0); rc != ADSB_AMD_OK)
             throw std::runtime_error(std::string("libadsb_amd: ") + adsb_amd_uat_last_error(nullptr));
+        TrackIfNoHostDecoder();
     }
     void StartTransport() { listener978.Start(this); } // UAT978.cpp:67
     void StopTransport() { listener978.Stop(); }       // :71
@@ -59,11 +64,24 @@ struct UAT978GpuHandler final : RTLSDR::IDataHandler, ADSB::IDataProvider, adsb_
     {
         if (int rc = adsb_amd_uat_create(&gpu, 0); rc != ADSB_AMD_OK)
             throw std::runtime_error(std::string("libadsb_amd: ") + adsb_amd_uat_last_error(nullptr));
+        TrackIfNoHostDecoder();
     }
     void StartTransport() { transport.Start(this); }
     void StopTransport() { transport.Stop(); }
     void Deliver(const uint8_t* data, size_t nbytes) override { HandleData(std::span<uint8_t const>(data, nbytes)); } // RTLSDR.hpp:531
 #endif
+    // (called from the constructors: a throw there skips the destructor, so the handle is released here first)
+    void TrackIfNoHostDecoder()
+    {
+        if (dump_raw_message) return;
+        if (adsb_amd_uat_set_tracking(gpu, &UAT978GpuHandler::OnUpdate, this, 0) != ADSB_AMD_OK)
+        {
+            const std::string what = std::string("libadsb_amd: ") + adsb_amd_uat_last_error(gpu);
+            adsb_amd_uat_destroy(gpu);
+            gpu = nullptr;
+            throw std::runtime_error(what);
+        }
+    }
     ~UAT978GpuHandler() override
     {
         StopTransport();
@@ -96,6 +114,22 @@ struct UAT978GpuHandler final : RTLSDR::IDataHandler, ADSB::IDataProvider, adsb_
         uint8_t copy[432];
         std::memcpy(copy, data, (size_t)len);
         dump_raw_message(updown, copy, len, rs_errors);
+    }
+
+    // uat2json-wrapper.cpp:18-121 on the decoded record
+    static void OnUpdate(void* user, const adsb_amd_uat_update_t* upd, const adsb_amd_aircraft_t* /*this handle's view*/)
+    {
+        auto* const               self = static_cast<UAT978GpuHandler*>(user);
+        const adsb_amd_uat_mdb_t& m    = upd->mdb;
+        auto&                     a    = self->trafficManager->FindOrCreate(m.address);
+        if (m.valid & ADSB_AMD_UAT_CALLSIGN) std::memcpy(a.callsign.data(), m.callsign, 8);
+        if (m.valid & ADSB_AMD_UAT_POSITION) a.lat1E7 = m.lat1e7, a.lon1E7 = m.lon1e7;
+        if (m.valid & ADSB_AMD_UAT_SPEED) a.speed = m.speed;
+        if (m.valid & ADSB_AMD_UAT_ALTITUDE) a.altitude = m.altitude;
+        if (m.valid & ADSB_AMD_UAT_TRACK) a.track = m.track;
+        if (m.valid & ADSB_AMD_UAT_VERTRATE) a.vertRate = m.vert_rate;
+        a.sourceId = ADSB::Source::UAT978;
+        self->trafficManager->NotifyChanged(a);
     }
 
     std::shared_ptr<ADSB::TrafficManager> trafficManager;

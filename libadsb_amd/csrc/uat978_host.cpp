@@ -7,9 +7,11 @@
 //                      clear its two shift registers when it does): a successor function over the ordered matches, resolved
 //                      by pointer jumping (uat_succ_kernel / uat_mark_kernel)
 //   host (this file)   the up-calls for the frames taken, in stream order, and UAT978Handler::HandleData's staging/re-buffering
-//                      (UAT978.cpp:43-60).  The scan loop itself is kept here as well (host_loop): it runs when a call needs more
-//                      than kUatExtraCap frames behind stale register bits, or when ADSB_AMD_UAT_HOST_LOOP=1 asks for it (tests
-//                      hold the two against each other).
+//                      (UAT978.cpp:43-60); on handles that track aircraft (adsb_amd_uat_set_tracking) also the sticky update of
+//                      uat2json-wrapper.cpp:18-121 per frame, from the record uat_mdb_kernel decoded (mdb978.h).  The scan
+//                      loop itself is kept here as well (host_loop): it runs when a call needs more than kUatExtraCap frames
+//                      behind stale register bits, or when ADSB_AMD_UAT_HOST_LOOP=1 asks for it (tests hold the two against
+//                      each other).
 //
 // The algorithm restated here is the published dump978 legacy demodulator; it is un-vendored in the reference tree
 // (SURVEY.md F7), so parity is unpinned: tests compare this path with oracle/oracle978.c on generated streams.
@@ -32,6 +34,7 @@
 #include <vector>
 
 #include "adsb_amd.h"
+#include "mdb978.h"
 #include "rs978.h"
 #include "scan1090.h"
 #include "uat978.h"
@@ -219,6 +222,19 @@ struct adsb_amd_uat
     uint64_t            part_n = 0;
     static constexpr uint32_t kExtraFirstCopy = 128; // extras fetched with the records; a call with more takes a second copy
 
+    // aircraft tracking (adsb_amd_uat_set_tracking).  track / want_frames are set on every side of the pipeline; the callback and the
+    // aircraft live on the handle the caller holds (`owner`; a twin's is that handle).
+    adsb_amd_uat*              owner = this;
+    bool                       track = false, want_frames = true;
+    adsb_amd_uat_on_changed_fn track_cb   = nullptr;
+    void*                      track_user = nullptr;
+    bool                       track_failed = false;
+    std::unordered_map<uint32_t, adsb_amd_aircraft_t> aircraft;
+    uat_mdb_t*       mdb_d = nullptr;       // parallel to recs_d: the decoded MDB of each record's frame
+    uint32_t         mdb_cap = 0;
+    uat_mdb_t*       extra_mdb_d = nullptr; // parallel to extras_d (kUatExtraCap)
+    Pinned<uat_mdb_t> mdb_h, extra_mdb_h;
+
     // input staging for host buffers
     uint8_t* in_d = nullptr;
     size_t   in_cap = 0;
@@ -240,7 +256,7 @@ struct adsb_amd_uat
         stop_pipeline();
         (void)hipSetDevice(device);
         for (void* p : {(void*)lut_d, (void*)rs_d, (void*)signs_d, (void*)cand_d, (void*)sorted_d, (void*)order_scratch_d, (void*)counts_d, (void*)demod_work_d, (void*)bin_fill_d[0], (void*)bin_fill_d[1], (void*)bin_slots_d, (void*)recs_d, (void*)wins_d, (void*)pay_d, (void*)up_d, (void*)in_d,
-                        (void*)stage_d, (void*)stage_tmp_d, (void*)next_bit_d, (void*)succ_d, (void*)exit_d, (void*)emit_d, (void*)marks_d, (void*)extras_d, (void*)extra_pay_d})
+                        (void*)stage_d, (void*)stage_tmp_d, (void*)next_bit_d, (void*)succ_d, (void*)exit_d, (void*)emit_d, (void*)marks_d, (void*)extras_d, (void*)extra_pay_d, (void*)mdb_d, (void*)extra_mdb_d})
             if (p) (void)hipFree(p);
         if (counts_h) (void)hipHostFree(counts_h);
         for (auto e : ev)
@@ -501,6 +517,28 @@ struct adsb_amd_uat
         a.cand    = sorted_d;
         const bool     decide = a.lenbits > 0;
         const uint32_t mark_words = (count + 31) / 32;
+        const bool     frames = !track || want_frames; // aircraft only: the frame bytes stay on the device
+        if (track)
+        {
+            if (count > mdb_cap)
+            {
+                if (mdb_d) (void)hipFree(mdb_d);
+                mdb_d = nullptr, mdb_cap = 0;
+                UAT_HIP(hipMalloc(&mdb_d, (size_t)count * sizeof(uat_mdb_t)));
+                mdb_cap = count;
+            }
+            if (!extra_mdb_d) UAT_HIP(hipMalloc(&extra_mdb_d, (size_t)kUatExtraCap * sizeof(uat_mdb_t)));
+            UAT_HIP(mdb_h.reserve(count, 0));
+            UAT_HIP(extra_mdb_h.reserve(kUatExtraCap, 0));
+        }
+        // tracking: the records' MDBs behind the demodulation pass (which also wrote the frames behind frames), on the call's stream
+        auto decode_mdbs = [&]() -> int
+        {
+            UAT_HIP(launch_uat978_mdb(a, count, mdb_d, extra_mdb_d, stream));
+            UAT_HIP(hipMemcpyAsync(mdb_h.p, mdb_d, (size_t)count * sizeof(uat_mdb_t), hipMemcpyDeviceToHost, stream));
+            UAT_HIP(hipMemcpyAsync(extra_mdb_h.p, extra_mdb_d, kExtraFirstCopy * sizeof(uat_mdb_t), hipMemcpyDeviceToHost, stream));
+            return ADSB_AMD_OK;
+        };
         if (in_pipeline)
         { // Calls in flight: everything behind the decision kernels, on the call's own stream, one wait.  (The copies of the other form set out
           // earlier but its counts -- sixteen bytes, which the runtime copies with a kernel -- have to get onto a chip that the other calls'
@@ -515,9 +553,10 @@ struct adsb_amd_uat
                 UAT_HIP(hipMemcpyAsync(extras_h.p, extras_d, kExtraFirstCopy * sizeof(uat_extra_t), hipMemcpyDeviceToHost, stream));
                 UAT_HIP(hipMemcpyAsync(extra_pay_h.p, extra_pay_d, (size_t)kExtraFirstCopy * kUatPayloadStride, hipMemcpyDeviceToHost, stream));
             }
+            if (track && decode_mdbs()) return ADSB_AMD_EHIP;
             UAT_HIP(hipMemcpyAsync(counts_h + 1, counts_d + 1, (kUatCountWords - 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             UAT_HIP(hipMemcpyAsync(recs_h.p, recs_d, (size_t)count * sizeof(uat_rec_t), hipMemcpyDeviceToHost, stream));
-            UAT_HIP(hipMemcpyAsync(pay_h.p, pay_d, (size_t)count * kUatPayloadStride, hipMemcpyDeviceToHost, stream));
+            if (frames) UAT_HIP(hipMemcpyAsync(pay_h.p, pay_d, (size_t)count * kUatPayloadStride, hipMemcpyDeviceToHost, stream));
             UAT_HIP(hipStreamSynchronize(stream));
             const uint32_t up_total = counts_h[kUatCountUplinkSlots];
             const bool     overflow = counts_h[kUatCountOverflow] != 0;
@@ -526,7 +565,7 @@ struct adsb_amd_uat
             nextras                = std::min<uint32_t>(counts_h[kUatCountExtras], extra_cap);
             decided                = decide && !overflow;
             bool more              = false;
-            if (up_have > nuplink)
+            if (frames && up_have > nuplink)
             {
                 UAT_HIP(up_h.reserve((size_t)up_have * 432, (size_t)nuplink * 432));
                 UAT_HIP(hipMemcpyAsync(up_h.p + (size_t)nuplink * 432, up_d + (size_t)nuplink * 432, (size_t)(up_have - nuplink) * 432,
@@ -541,6 +580,9 @@ struct adsb_amd_uat
                                        hipMemcpyDeviceToHost, stream));
                 UAT_HIP(hipMemcpyAsync(extra_pay_h.p + (size_t)kExtraFirstCopy * kUatPayloadStride, extra_pay_d + (size_t)kExtraFirstCopy * kUatPayloadStride,
                                        (size_t)(nextras - kExtraFirstCopy) * kUatPayloadStride, hipMemcpyDeviceToHost, stream));
+                if (track)
+                    UAT_HIP(hipMemcpyAsync(extra_mdb_h.p + kExtraFirstCopy, extra_mdb_d + kExtraFirstCopy, (size_t)(nextras - kExtraFirstCopy) * sizeof(uat_mdb_t),
+                                           hipMemcpyDeviceToHost, stream));
                 more = true;
             }
             if (more) UAT_HIP(hipStreamSynchronize(stream));
@@ -560,7 +602,7 @@ struct adsb_amd_uat
             // twins (calls in flight) never use shifted the twins' compute streams onto one queue: 0.43 -> 0.55 ms per pipelined step inside bench.py
             if (!copy_stream2) UAT_HIP(hipStreamCreateWithFlags(&copy_stream2, hipStreamNonBlocking));
             UAT_HIP(hipStreamWaitEvent(copy_stream2, ev_demod, 0));
-            UAT_HIP(hipMemcpyAsync(pay_h.p, pay_d, (size_t)count * kUatPayloadStride, hipMemcpyDeviceToHost, copy_stream2));
+            if (frames) UAT_HIP(hipMemcpyAsync(pay_h.p, pay_d, (size_t)count * kUatPayloadStride, hipMemcpyDeviceToHost, copy_stream2));
             UAT_HIP(hipEventRecord(ev_copy2, copy_stream2));
             if (decide)
             {
@@ -574,6 +616,7 @@ struct adsb_amd_uat
                 UAT_HIP(hipMemcpyAsync(marks_h.p, marks_d, mark_words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
                 UAT_HIP(hipMemcpyAsync(counts_h + kUatCountFinalBit, counts_d + kUatCountFinalBit, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             }
+            if (track && decode_mdbs()) return ADSB_AMD_EHIP;
             // (3) as soon as the counts are here: the uplink payloads and the frames behind frames beyond the first copy, still beside the decisions
             UAT_HIP(hipEventSynchronize(ev_counts));
             const uint32_t up_total = counts_h[kUatCountUplinkSlots];
@@ -588,7 +631,7 @@ struct adsb_amd_uat
             const uint32_t up_have = std::min(up_total, up_cap);
             nextras                = std::min<uint32_t>(counts_h[kUatCountExtras], extra_cap);
             decided                = decide && !overflow;
-            if (up_have > nuplink)
+            if (frames && up_have > nuplink)
             {
                 UAT_HIP(up_h.reserve((size_t)up_have * 432, (size_t)nuplink * 432));
                 UAT_HIP(hipMemcpyAsync(up_h.p + (size_t)nuplink * 432, up_d + (size_t)nuplink * 432, (size_t)(up_have - nuplink) * 432,
@@ -604,6 +647,9 @@ struct adsb_amd_uat
                                        hipMemcpyDeviceToHost, copy_stream));
                 UAT_HIP(hipMemcpyAsync(extra_pay_h.p + (size_t)kExtraFirstCopy * kUatPayloadStride, extra_pay_d + (size_t)kExtraFirstCopy * kUatPayloadStride,
                                        (size_t)(nextras - kExtraFirstCopy) * kUatPayloadStride, hipMemcpyDeviceToHost, copy_stream));
+                if (track)
+                    UAT_HIP(hipMemcpyAsync(extra_mdb_h.p + kExtraFirstCopy, extra_mdb_d + kExtraFirstCopy, (size_t)(nextras - kExtraFirstCopy) * sizeof(uat_mdb_t),
+                                           hipMemcpyDeviceToHost, stream));
             }
             UAT_HIP(hipStreamSynchronize(copy_stream));
             UAT_HIP(hipEventSynchronize(ev_copy2));
@@ -721,11 +767,13 @@ struct adsb_amd_uat
         const int64_t lenbits = (int64_t)(len / 2) - (kUatSyncBits + kUatUplinkBits);
         if (host_loop_only || (nmain && lenbits > 0 && !decided)) return host_loop(in_dev, len, phases_given, stream_offset, cb, user, consumed);
         const double t_loop = now_ms();
-        auto emit = [&](const uat_rec_t& r, const uint8_t* adsb_bytes)
+        if (track && !want_frames) cb = nullptr; // aircraft only: the frame bytes are not on the host
+        auto emit = [&](const uat_rec_t& r, const uint8_t* adsb_bytes, const uat_mdb_t& m)
         {
             const uint8_t* data = r.kind ? up_h.p + (size_t)r.slot * 432 : adsb_bytes;
             const int      n    = r.kind ? 432 : r.skip == kUatShortSkip ? 18 : 34;
-            cb(user, r.kind ? '+' : '-', data, n, r.rs, stream_offset + r.index + (uint64_t)r.variant);
+            if (cb) cb(user, r.kind ? '+' : '-', data, n, r.rs, stream_offset + r.index + (uint64_t)r.variant);
+            if (track) owner->track_frame(r.kind ? '+' : '-', r.rs, stream_offset + r.index + (uint64_t)r.variant, m);
         };
         if (decided)
         {
@@ -737,7 +785,7 @@ struct adsb_amd_uat
                 return a.parent != b.parent ? a.parent < b.parent : a.seq < b.seq;
             });
             auto taken = [&](uint32_t k) { return (marks_h.p[k >> 5] >> (k & 31u)) & 1u; };
-            if (cb)
+            if (cb || track)
             {
                 size_t         xe    = 0;
                 const uint32_t words = (nmain + 31) / 32;
@@ -745,10 +793,11 @@ struct adsb_amd_uat
                     for (uint32_t bits = marks_h.p[w]; bits; bits &= bits - 1)
                     {
                         const uint32_t k = w * 32 + (uint32_t)__builtin_ctz(bits);
-                        emit(recs_h.p[k], pay_h.p + (size_t)k * kUatPayloadStride);
+                        emit(recs_h.p[k], pay_h.p + (size_t)k * kUatPayloadStride, mdb_h.p[k]);
                         while (xe < order.size() && extras_h.p[order[xe]].parent < k) xe++;
                         for (; xe < order.size() && extras_h.p[order[xe]].parent == k; xe++)
-                            if (extras_h.p[order[xe]].rec.variant < 2) emit(extras_h.p[order[xe]].rec, extra_pay_h.p + (size_t)order[xe] * kUatPayloadStride);
+                            if (extras_h.p[order[xe]].rec.variant < 2)
+                                emit(extras_h.p[order[xe]].rec, extra_pay_h.p + (size_t)order[xe] * kUatPayloadStride, extra_mdb_h.p[order[xe]]);
                     }
             }
             for (uint32_t x : order)
@@ -763,7 +812,7 @@ struct adsb_amd_uat
         const int64_t final_bit = decided ? (int64_t)counts_h[kUatCountFinalBit] : 0;
         *consumed  = lenbits > 0 ? (std::max(final_bit, lenbits) - kUatCheckBits) * 2 : (int64_t)-2 * kUatCheckBits;
         wall_ms[3] = (float)(now_ms() - t_loop);
-        return ADSB_AMD_OK;
+        return track ? owner->track_status() : ADSB_AMD_OK;
     }
 
     // the dump978 scan loop on the host, over the records scan() left in recs_h (see the top of the file for when it runs)
@@ -786,9 +835,16 @@ struct adsb_amd_uat
         size_t  pos = 0;
         auto rec_at  = [&](size_t k) -> const uat_rec_t& { return recs_h.p[k]; };
         const size_t nordered = nmain;
+        if (track && !want_frames) cb = nullptr;
         auto emit = [&](const uat_rec_t& r, const Attempt& a)
         {
             if (cb) cb(user, r.kind ? '+' : '-', a.data, a.len, a.rs, stream_offset + r.index + (uint64_t)a.variant);
+            if (track)
+            { // a match of the list: decoded on the device; a position the loop asked for on its own: its bytes are here, decode them here
+                const size_t k = (size_t)(&r - recs_h.p);
+                owner->track_frame(r.kind ? '+' : '-', a.rs, stream_offset + r.index + (uint64_t)a.variant,
+                                   k < nmain ? mdb_h.p[k] : decode_mdb_bytes(a.data, a.len));
+            }
         };
 
         while (bit < lenbits)
@@ -870,7 +926,41 @@ struct adsb_amd_uat
         if (bit < lenbits) bit = lenbits; // no further match: the loop runs to the end
         *consumed = lenbits > 0 ? (bit - kUatCheckBits) * 2 : (int64_t)-2 * kUatCheckBits;
         wall_ms[3] = (float)(now_ms() - t_loop);
-        return ADSB_AMD_OK;
+        return track ? owner->track_status() : ADSB_AMD_OK;
+    }
+
+    // ---------------------------------------------------------------------------------------------------------------
+    // Aircraft tracking: uat2json-wrapper.cpp:18-121 per reported frame -- FindOrCreate by address, copy what the update marks
+    // valid (the call sign only as CS_CALLSIGN, 8 bytes), squawk stays 0 -- then the callback with the update and the aircraft.
+    // ---------------------------------------------------------------------------------------------------------------
+    void track_frame(char updown, int rs, uint64_t sample_index, const uat_mdb_t& m)
+    {
+        adsb_amd_aircraft_t* a = nullptr;
+        try
+        {
+            a = &aircraft.try_emplace(m.address).first->second;
+        }
+        catch (...)
+        {
+            track_failed = true;
+            return;
+        }
+        a->addr = m.address;
+        if (m.valid & ADSB_AMD_UAT_POSITION) a->lat1e7 = m.lat1e7, a->lon1e7 = m.lon1e7;
+        if (m.valid & ADSB_AMD_UAT_SPEED) a->speed = m.speed;
+        if (m.valid & ADSB_AMD_UAT_ALTITUDE) a->altitude = m.altitude;
+        if (m.valid & ADSB_AMD_UAT_TRACK) a->track = m.track;
+        if (m.valid & ADSB_AMD_UAT_VERTRATE) a->vert_rate = m.vert_rate;
+        if (m.valid & ADSB_AMD_UAT_CALLSIGN) std::memcpy(a->callsign, m.callsign, 8);
+        adsb_amd_uat_update_t u{};
+        u.sample_index = sample_index, u.rs_errors = rs, u.updown = updown, u.mdb = m;
+        if (track_cb) track_cb(track_user, &u, a);
+    }
+    int track_status()
+    {
+        if (!track_failed) return ADSB_AMD_OK;
+        track_failed = false;
+        return fail(ADSB_AMD_ENOMEM, "UAT tracking: out of host memory for the aircraft table");
     }
 
     // ---------------------------------------------------------------------------------------------------------------
@@ -990,6 +1080,7 @@ struct adsb_amd_uat
                 twin->device = device;
                 twin->host_loop_only = host_loop_only;
                 twin->extra_cap = extra_cap;
+                twin->owner = this, twin->track = track, twin->want_frames = want_frames;
                 const int rc = twin->init(pipe_stream[t + 1]);
                 if (rc)
                 {
@@ -1272,6 +1363,64 @@ extern "C" int adsb_amd_uat_rs_decode(int kind, uint8_t* codeword)
     RsWork w;
     return kind == 0 ? rs978_decode(rs_tables(), 12, 225, codeword, 1, w)
                      : kind == 1 ? rs978_decode(rs_tables(), 14, 207, codeword, 1, w) : rs978_decode(rs_tables(), 20, 163, codeword, 1, w);
+}
+
+extern "C" int adsb_amd_uat_set_tracking(adsb_amd_uat_t* u, adsb_amd_uat_on_changed_fn cb, void* user, int want_frames)
+{
+    if (!u) return ADSB_AMD_EINVAL;
+    if (u->calls_in_flight()) return u->fail(ADSB_AMD_ESTATE, "UAT calls are in flight: collect them first");
+    u->track = cb != nullptr, u->want_frames = !cb || want_frames != 0;
+    u->track_cb = cb, u->track_user = user;
+    for (auto& t : u->twins)
+        if (t) t->track = u->track, t->want_frames = u->want_frames;
+    return ADSB_AMD_OK;
+}
+extern "C" int adsb_amd_uat_aircraft_count(const adsb_amd_uat_t* u, uint64_t* count)
+{
+    if (!u || !count) return ADSB_AMD_EINVAL;
+    *count = u->aircraft.size();
+    return ADSB_AMD_OK;
+}
+extern "C" int adsb_amd_uat_reset_aircraft(adsb_amd_uat_t* u)
+{
+    if (!u) return ADSB_AMD_EINVAL;
+    if (u->calls_in_flight()) return u->fail(ADSB_AMD_ESTATE, "UAT calls are in flight: collect them first");
+    u->aircraft.clear();
+    return ADSB_AMD_OK;
+}
+extern "C" int adsb_amd_uat_mdb_decode(const uint8_t* frames, int count, int stride, adsb_amd_uat_mdb_t* out)
+{ // the decoder uat_mdb_kernel runs (mdb978.h), compiled for the host
+    if (count < 0 || stride <= 0 || (count && (!frames || !out))) return ADSB_AMD_EINVAL;
+    for (int i = 0; i < count; i++) out[i] = decode_mdb_bytes(frames + (size_t)i * stride, stride);
+    return ADSB_AMD_OK;
+}
+extern "C" int adsb_amd_uat_mdb_decode_device(adsb_amd_uat_t* u, const uint8_t* frames, int count, int stride, adsb_amd_uat_mdb_t* out)
+{
+    if (!u || count < 0 || stride <= 0 || (count && (!frames || !out))) return ADSB_AMD_EINVAL;
+    if (count == 0) return ADSB_AMD_OK;
+    if (u->calls_in_flight()) return u->fail(ADSB_AMD_ESTATE, "UAT calls are in flight: collect them first");
+    try
+    {
+        if (hipSetDevice(u->device) != hipSuccess) return u->fail(ADSB_AMD_EHIP, "hipSetDevice failed");
+        const size_t bytes = (size_t)count * (size_t)stride;
+        uint8_t*     f_d   = nullptr;
+        uat_mdb_t*   o_d   = nullptr;
+        auto&        error = u->error;
+        UAT_HIP(hipMalloc(&f_d, bytes));
+        hipError_t e = hipMalloc(&o_d, (size_t)count * sizeof(uat_mdb_t));
+        if (e == hipSuccess) e = hipMemcpy(f_d, frames, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = launch_uat978_mdb_selftest(f_d, (uint32_t)count, (uint32_t)stride, o_d, u->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(u->stream);
+        if (e == hipSuccess) e = hipMemcpy(out, o_d, (size_t)count * sizeof(uat_mdb_t), hipMemcpyDeviceToHost);
+        (void)hipFree(f_d);
+        if (o_d) (void)hipFree(o_d);
+        UAT_HIP(e);
+        return ADSB_AMD_OK;
+    }
+    catch (...)
+    {
+        return u->fail(ADSB_AMD_EHIP, "adsb_amd_uat_mdb_decode_device: exception");
+    }
 }
 
 // ---- the reference's C seam (UAT978.cpp:9-10): same names, same meaning.  dump_raw_message is the host's
